@@ -149,6 +149,33 @@ def load():
     return lib
 
 
+# The MixStyle extension ABI (include/ccst_mixstyle.h): the same library, its own version and signature table, so that EXPORTS
+# stays the core header's symbol set.
+MIXSTYLE_ABI_VERSION = 1
+_MIXSTYLE_SIGNATURES = {
+    "ccst_mixstyle_abi_version": [],
+    "ccst_mixstyle_fwd_f32": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, c_int64, _P, _P],
+    "ccst_mixstyle_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P],
+}
+MIXSTYLE_EXPORTS = tuple(_MIXSTYLE_SIGNATURES)
+_mixstyle_bound = False
+
+
+def load_mixstyle():
+    """load() with the MixStyle entry points bound; raise if the library's extension version is not MIXSTYLE_ABI_VERSION."""
+    global _mixstyle_bound
+    lib = load()
+    if not _mixstyle_bound:
+        for name, argtypes in _MIXSTYLE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        if lib.ccst_mixstyle_abi_version() != MIXSTYLE_ABI_VERSION:
+            raise RuntimeError("ccst_amd: MixStyle extension ABI version mismatch")
+        _mixstyle_bound = True
+    return lib
+
+
 def check(rc, what):
     if rc != 0:
         msg = load().ccst_last_error()

@@ -27,7 +27,7 @@ def _sources():
 def _digest():
     h = hashlib.sha256()
     for f in _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + \
-            [os.path.join(os.path.dirname(HERE), "include", "ccst_hip.h")]:
+            sorted(glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h"))):
         with open(f, "rb") as fh:
             h.update(f.encode())
             h.update(fh.read())

@@ -13,6 +13,7 @@
 //              CCST_OverallStyleTransfer.py:45), one read + one write of the tensor.
 // layout 0 = NCHW planes (API tensors), 1 = NHWC (the pipeline's internal layout).
 #include "common.h"
+#include "../../include/ccst_mixstyle.h"
 
 namespace {
 
@@ -563,6 +564,80 @@ __global__ __launch_bounds__(TPB) void adain_stream_nhwc_kernel(const float* __r
     if (ymax != nullptr) ccst_absmax_publish(ymax, amax, bid_, peeked);
 }
 
+// MixStyle (nets/layers.py:36-73) on NHWC, the streaming pass: adain_stream_nhwc_kernel's tiling (image n x 16 channel quads x 256
+// pixels per workgroup), with the target statistics mixed in registers from image n's and image perm[n]'s:
+//     mu_mix = mu lam + mu[perm] (1 - lam),   sigma_mix likewise      (separately rounded fp32 operations, 1 - lam rounded once)
+//   forward : y = ((x - mu) / sigma) sigma_mix + mu_mix               (sub, div, mul, add as adain_one orders them, no contraction)
+//   backward: dx = (dy sigma_mix) / sigma                              (mu, sigma are detached: autograd's MulBackward, then DivBackward)
+// The arithmetic is spelled out under `fp contract(off)`: adain_one's __fmul_rn / __fadd_rn are plain inline operations in HIP, and at
+// -O3 the compiler fuses its mul + add into one FMA (measured: 30 % of the outputs one rounding away from the four-operation result).
+// C % 4 == 0 (a quad past C idles).  perm[n] outside [0, N) -- which the host side refuses -- reads image n's statistics and poisons
+// image n's output with NaN instead of reading out of bounds.  ymax: per-TENSOR |max| words of y (the ResNet-side convention).
+__device__ __forceinline__ float mixstyle_mix(float a, float b, float l, float oml) {
+#pragma clang fp contract(off)
+    return a * l + b * oml;
+}
+__device__ __forceinline__ float mixstyle_one(float x, float mu, float sd, float sm, float ss) {
+#pragma clang fp contract(off)
+    return ((x - mu) / sd) * ss + sm;
+}
+__device__ __forceinline__ float mixstyle_grad(float dy, float sd, float ss) {
+#pragma clang fp contract(off)
+    return (dy * ss) / sd;
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(TPB) void mixstyle_stream_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                   const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                   const float* __restrict__ lam, const int* __restrict__ perm, int N, int HW,
+                                                                   int C, unsigned* __restrict__ ymax) {
+    const int t = threadIdx.x, cq = t % TS_CQ, pl = t / TS_CQ;
+    const int n = blockIdx.y, c0 = blockIdx.x * (4 * TS_CQ) + cq * 4;
+    const bool live = c0 < C;
+    const float* xb = x + ((long long)n * HW) * C + c0;
+    float* yb = y + ((long long)n * HW) * C + c0;
+    const int p0 = blockIdx.z * TS_PIX;
+    f32x4 v[TS_PIX / TS_PL];
+#pragma unroll
+    for (int i = 0; i < TS_PIX / TS_PL; ++i) {
+        const int p = p0 + pl + i * TS_PL;
+        if (live && p < HW) v[i] = *reinterpret_cast<const f32x4*>(xb + (long long)p * C);
+    }
+    int m = perm[n];
+    const bool bad = (unsigned)m >= (unsigned)N;
+    if (bad) m = n;
+    const float l = lam[n], oml = 1.f - l;
+    f32x4 sd = {1.f, 1.f, 1.f, 1.f}, ss = {1.f, 1.f, 1.f, 1.f}, mu = {0.f, 0.f, 0.f, 0.f}, sm = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        sd = *reinterpret_cast<const f32x4*>(stdv + (long long)n * C + c0);
+        const f32x4 sd2 = *reinterpret_cast<const f32x4*>(stdv + (long long)m * C + c0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ss[j] = bad ? __builtin_nanf("") : mixstyle_mix(sd[j], sd2[j], l, oml);
+        if (!BWD) {
+            mu = *reinterpret_cast<const f32x4*>(mean + (long long)n * C + c0);
+            const f32x4 mu2 = *reinterpret_cast<const f32x4*>(mean + (long long)m * C + c0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sm[j] = mixstyle_mix(mu[j], mu2[j], l, oml);
+        }
+    }
+    float amax = 0.f;
+    const unsigned bid_ = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const unsigned peeked = ymax != nullptr ? ccst_absmax_peek(ymax, bid_) : 0u;
+#pragma unroll
+    for (int i = 0; i < TS_PIX / TS_PL; ++i) {
+        const int p = p0 + pl + i * TS_PL;
+        if (live && p < HW) {
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                o[j] = BWD ? mixstyle_grad(v[i][j], sd[j], ss[j]) : mixstyle_one(v[i][j], mu[j], sd[j], sm[j], ss[j]);
+            amax = fmaxf(fmaxf(fmaxf(amax, fabsf(o[0])), fmaxf(fabsf(o[1]), fabsf(o[2]))), fabsf(o[3]));
+            *reinterpret_cast<f32x4*>(yb + (long long)p * C) = o;
+        }
+    }
+    if (ymax != nullptr) ccst_absmax_publish(ymax, amax, bid_, peeked);
+}
+
 // CCST_OverallStyleTransfer.py:36-45, the interpolation branch: feat = sum_k w_k * base[k] (accumulated in the reference's order, from
 // zero, every product and sum rounded separately), then feat * alpha + content[0] * (1 - alpha).  Elementwise, so any layout.
 __global__ __launch_bounds__(TPB) void interp_blend_kernel(const float* __restrict__ base, const float* __restrict__ content0,
@@ -716,4 +791,49 @@ extern "C" int ccst_chan_sums_f32(const float* x, float* sum, float* sqsum, int 
     if (rc) return rc;
     hipLaunchKernelGGL(finalize_chan_sums_kernel<false>, dim3((C + 15) / 16), dim3(256), 0, st, part, sum, sqsum, N, C, S);
     return ccst_launch_status("finalize_chan_sums");
+}
+
+// ---- MixStyle (include/ccst_mixstyle.h) ---------------------------------------------------------------------------------------------------
+extern "C" int ccst_mixstyle_abi_version(void) { return CCST_MIXSTYLE_ABI_VERSION; }
+
+static int mixstyle_check(const void* x, const float* stdv, const float* lam, const int32_t* perm, const void* y, int N, int C, int HW,
+                          const char* what) {
+    CCST_REQUIRE(x && stdv && lam && perm && y, "%s: null pointer", what);
+    CCST_REQUIRE(N > 0 && N <= 65535 && C > 0 && C % 4 == 0 && HW > 0, "%s: bad shape N=%d C=%d HW=%d (NHWC, C %% 4 == 0)", what, N, C, HW);
+    CCST_REQUIRE((HW + TS_PIX - 1) / TS_PIX <= 65535 && (long long)N * C * 2 <= 0x7fffffffLL, "%s: tensor too large", what);
+    CCST_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)stdv) % 16 == 0, "%s: tensors and statistics must be 16-byte aligned", what);
+    return CCST_OK;
+}
+
+extern "C" int ccst_mixstyle_fwd_f32(const float* x, const float* lam, const int32_t* perm, float* y, float* mean, float* stdv, int N, int C,
+                                     int HW, float eps, void* ws, int64_t ws_bytes, uint32_t* y_absmax, void* stream) {
+    int rc = mixstyle_check(x, stdv, lam, perm, y, N, C, HW, "mixstyle_fwd");
+    if (rc) return rc;
+    CCST_REQUIRE(mean && ws && (uintptr_t)mean % 16 == 0, "mixstyle_fwd: null or misaligned mean / workspace");
+    if (ws_bytes < ccst_stats_workspace_bytes(N, C, HW)) {
+        ccst_set_error("mixstyle_fwd: workspace %lld < %lld", (long long)ws_bytes, (long long)ccst_stats_workspace_bytes(N, C, HW));
+        return CCST_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // the statistics exactly as ccst_calc_mean_std_f32 computes them: the split count is a function of the plane only, so a sample's
+    // mu / sigma do not depend on its batch-mates
+    const int S = pick_splits(1, C, HW, 1);
+    float* part = (float*)ws;
+    rc = run_partials<true>(x, part, N, C, HW, 1, S, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(finalize_mean_std_kernel, dim3((N * C + 15) / 16), dim3(256), 0, st, x, part, mean, stdv, N, C, S, HW, 1, eps);
+    rc = ccst_launch_status("mixstyle finalize");
+    if (rc) return rc;
+    hipLaunchKernelGGL(mixstyle_stream_nhwc_kernel<false>, dim3((C + 4 * TS_CQ - 1) / (4 * TS_CQ), N, (HW + TS_PIX - 1) / TS_PIX), dim3(TPB), 0, st,
+                       x, y, mean, stdv, lam, perm, N, HW, C, y_absmax);
+    return ccst_launch_status("mixstyle_fwd");
+}
+
+extern "C" int ccst_mixstyle_bwd_f32(const float* dy, const float* stdv, const float* lam, const int32_t* perm, float* dx, int N, int C, int HW,
+                                     void* stream) {
+    int rc = mixstyle_check(dy, stdv, lam, perm, dx, N, C, HW, "mixstyle_bwd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(mixstyle_stream_nhwc_kernel<true>, dim3((C + 4 * TS_CQ - 1) / (4 * TS_CQ), N, (HW + TS_PIX - 1) / TS_PIX), dim3(TPB), 0,
+                       (hipStream_t)stream, dy, dx, nullptr, stdv, lam, perm, N, HW, C, nullptr);
+    return ccst_launch_status("mixstyle_bwd");
 }

@@ -313,8 +313,14 @@ class _LoopTimer(object):
         return ms
 
 
+def _draws_per_step(model):
+    """Does a train step of this model make host-side random draws (an activated MixStyle)?"""
+    from .nets.layers import MixStyle
+    return any(isinstance(m, MixStyle) and m._activated for m in model.modules())
+
+
 def train(model, train_loader, optimizer, loss_fun, client_num, device, args, iter_idx, logger):
-    if _dg(args) in ("rsc", "jigsaw", "mixstyle"):
+    if _dg(args) in ("rsc", "jigsaw"):
         raise NotImplementedError("ccst_amd.fed: --dg_method %s is outside the hot path" % args.dg_method)
     model.to(device)
     model.train()
@@ -323,7 +329,8 @@ def train(model, train_loader, optimizer, loss_fun, client_num, device, args, it
     correct_all = torch.zeros((), device=device, dtype=torch.int64)
     it = -1
     fused_acc = isinstance(loss_fun, CrossEntropyLoss)
-    use_graph = _graph_wanted(args) and fused_acc and logger is None and isinstance(optimizer, SGD)
+    # (a replay would freeze an active MixStyle's host-side draws -- gate, lambda, perm -- at the captured ones: such a model trains eagerly)
+    use_graph = _graph_wanted(args) and fused_acc and logger is None and isinstance(optimizer, SGD) and not _draws_per_step(model)
     auto = use_graph and _graph_mode(args) == "auto"
     if use_graph:
         # Captured steps hold raw addresses of the parameter arena.  model.to() above (args.offload_models moves the model to the

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .. import nn_ops, ops
+from .layers import MixStyle
 
 
 def _to_nhwc(x):
@@ -419,19 +420,52 @@ def _maybe_pretrained(model, name, pretrained):
     return model
 
 
+class MixStyleResNet(ResNet):
+    """nets/resnet.py:281-311: MixStyle after the named layers of the trunk.  The same state-dict keys as ResNet (MixStyle holds no
+    state).  A MixStyle output is a new tensor, so no gradient short-cut (MaskLink, GradSink) crosses it: the BatchNorm that closes
+    the layer applies its own ReLU mask in its backward.  When the gate leaves x unchanged, nothing differs from ResNet."""
+
+    def __init__(self, block, layers, classes=100, mixstyle_layers=[], mixstyle_p=0.5, mixstyle_alpha=0.1):
+        super(MixStyleResNet, self).__init__(block, layers, classes)
+        self.mixstyle = None
+        if mixstyle_layers:
+            self.mixstyle = MixStyle(p=mixstyle_p, alpha=mixstyle_alpha, mix='random')
+            print('Insert MixStyle after the following layers: {}'.format(mixstyle_layers))
+        self.mixstyle_layers = mixstyle_layers
+
+    def forward(self, x, **kwargs):
+        if self.training:
+            self._bump_counters()
+        x = self._stem(x)
+        for name in ("layer1", "layer2", "layer3"):
+            x = getattr(self, name)(x)
+            if name in self.mixstyle_layers:
+                x = self.mixstyle(x)
+        x = self.layer4(x)
+        x = self.avgpool(x)
+        x = x.view(x.size(0), -1)
+        return self.class_classifier(x)
+
+
 def _unsupported(args):
     dg = getattr(args, "dg_method", "") or ""
-    if dg.lower() in ("jigsaw", "mixstyle"):
+    if dg.lower() == "jigsaw":
         raise NotImplementedError("ccst_amd.nets: --dg_method %s is outside the hot path (SURVEY.md section 2)" % dg)
+
+
+def _build(args, block, layers, **kwargs):
+    """nets/resnet.py:326-331,350-355: MixStyleResNet with MixStyle after layer1..3 for --dg_method MixStyle, else ResNet."""
+    _unsupported(args)
+    if (getattr(args, "dg_method", "") or "").lower() == "mixstyle":
+        return MixStyleResNet(block, layers, mixstyle_layers=['layer1', 'layer2', 'layer3'], **kwargs)
+    return ResNet(block, layers, **kwargs)
 
 
 def resnet18(args, pretrained=True, **kwargs):
     """Constructs a ResNet-18 model (nets/resnet.py:326-345)."""
-    _unsupported(args)
-    return _maybe_pretrained(ResNet(BasicBlock, [2, 2, 2, 2], **kwargs), "resnet18", pretrained)
+    return _maybe_pretrained(_build(args, BasicBlock, [2, 2, 2, 2], **kwargs), "resnet18", pretrained)
 
 
 def resnet50(args, pretrained=True, **kwargs):
     """Constructs a ResNet-50 model (nets/resnet.py:350-370)."""
-    _unsupported(args)
-    return _maybe_pretrained(ResNet(Bottleneck, [3, 4, 6, 3], **kwargs), "resnet50", pretrained)
+    return _maybe_pretrained(_build(args, Bottleneck, [3, 4, 6, 3], **kwargs), "resnet50", pretrained)

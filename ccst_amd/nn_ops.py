@@ -859,3 +859,19 @@ class CrossEntropyFn(torch.autograd.Function):
         out = torch.empty_like(dlog)
         check(_lib.load().ccst_mul_scalar_f32(ptr(out), ptr(dlog), ptr(g.contiguous()), dlog.numel(), stream_ptr()), "ce_backward_scale")
         return out, None, None
+
+
+class MixStyleFn(torch.autograd.Function):
+    """MixStyle in training (nets/layers.py:44-73) on NHWC: the statistics are detached, so the backward is dx = (dy sigma_mix) / sigma.
+    Saves mean / sigma [2, N*C] and the draws (lambda bits | perm, int32 [2N] on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, draws, eps):
+        y, stat = ops.mixstyle_fwd(x, draws, eps)
+        ctx.save_for_backward(stat, draws)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        stat, draws = ctx.saved_tensors
+        return ops.mixstyle_bwd(dy, stat, draws), None, None

@@ -1080,3 +1080,34 @@ def chan_sums(feat):
         e1.record()
         TIMING.append(("chan_sums", 0.0, e0, e1, "n%d c%d hw%d bytes%d" % (N, C, H * W, 4 * N * C * H * W)))
     return s, q, N * H * W
+
+
+# ---------------------------------------------------------------------------
+# MixStyle (include/ccst_mixstyle.h)
+# ---------------------------------------------------------------------------
+def mixstyle_fwd(x, draws, eps=1e-6):
+    """MixStyle's training forward on an NHWC-contiguous [N,H,W,C] CUDA tensor (nets/layers.py:44-73).  draws: int32 [2N] on the
+    device -- lambda's fp32 bits, then perm.  Returns (y [N,H,W,C] tagged with its per-tensor |max| words, stat [2, N*C] = mean |
+    sigma, kept for mixstyle_bwd)."""
+    _require_cuda(x, "input")
+    N, H, W, C = x.shape
+    if C % 4 != 0 or not x.is_contiguous():
+        raise RuntimeError("ccst_amd: MixStyle needs an NHWC-contiguous tensor with C %% 4 == 0 (C=%d)" % C)
+    assert draws.dtype == torch.int32 and draws.numel() == 2 * N and draws.device == x.device
+    y = torch.empty_like(x)
+    stat = torch.empty((2, N * C), device=x.device, dtype=torch.float32)
+    ws, nb = _stats_ws(N, C, H * W, x.device)
+    words = absmax_words(x.device)      # max |y|: the next layer's half-piece convs scale their input by it
+    check(_lib.load_mixstyle().ccst_mixstyle_fwd_f32(ptr(x), ptr(draws[:N]), ptr(draws[N:]), ptr(y), ptr(stat[0]), ptr(stat[1]), N, C, H * W,
+                                                     float(eps), ptr(ws), nb, ptr(words), stream_ptr()), "mixstyle_fwd")
+    return tag_absmax(y, words), stat
+
+
+def mixstyle_bwd(dy, stat, draws):
+    """dx = (dy * sigma_mix) / sigma for mixstyle_fwd's statistics and draws (one streaming launch)."""
+    dy = dy.contiguous()
+    N, H, W, C = dy.shape
+    dx = torch.empty_like(dy)
+    check(_lib.load_mixstyle().ccst_mixstyle_bwd_f32(ptr(dy), ptr(stat[1]), ptr(draws[:N]), ptr(draws[N:]), ptr(dx), N, C, H * W, stream_ptr()),
+          "mixstyle_bwd")
+    return dx

@@ -11,7 +11,8 @@ Two launch forms
                                                          all-reduce of the flat fp32 state per global round.
 --mode fedbn (fed_run.py:388-399, :693-698, :735-759): clients keep every state entry whose key contains 'bn',
 are validated with their local model, and checkpoints also carry 'model_{k}' state dicts.
-Out of scope: adafea / fedprox aggregation variants, RSC / Jigsaw / MixStyle /
+--dg_method MixStyle (nets/resnet.py:281-311): MixStyle after layer1..3 of the ResNet, trained eagerly (never HIP-graph captured).
+Out of scope: adafea / fedprox aggregation variants, RSC / Jigsaw /
 FedDG, Tent, tensorboard / Excel logging."""
 import argparse
 import copy
@@ -102,8 +103,8 @@ def main():
     args = parse()
     if args.tent_test or getattr(args, 'tent_test_on-the-fly', False) or getattr(args, 'tent_test_on_the_fly', False):
         raise NotImplementedError("--tent_test / --tent_test_on-the-fly (Tent test-time optimisation, fed_run.py:591-624) are outside the hot path")
-    if args.mode.lower() not in ('fedavg', 'fedbn', 'deepall') or args.dg_method not in ('no_DG',):
-        raise NotImplementedError("only --mode fedavg/fedbn/deepall with --dg_method no_DG is on the hot path")
+    if args.mode.lower() not in ('fedavg', 'fedbn', 'deepall') or args.dg_method not in ('no_DG', 'MixStyle'):
+        raise NotImplementedError("only --mode fedavg/fedbn/deepall with --dg_method no_DG or MixStyle is on the hot path")
     if not torch.cuda.is_available():
         raise SystemExit("ccst_amd: an MI355X (ROCm) device is required; there is no CPU path")
     world = int(os.environ.get("WORLD_SIZE", "1"))

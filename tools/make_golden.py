@@ -176,13 +176,14 @@ sys.path.insert(0, REF)
 from nets import resnet as ref_resnet   # noqa: E402  (reference module: ResNet class, _make_layer, forward)
 
 
-def _run_case(model, x, y, lr):
+def _run_case(model, x, y, lr, train_seed=None):
     model.eval()
     with torch.no_grad():
         logit_eval = model(x)
     model.train()
     opt = torch.optim.SGD(model.parameters(), lr=lr)
     opt.zero_grad()
+    _seed_train(train_seed)
     logit_train = model(x)
     loss = nn.CrossEntropyLoss()(logit_train, y)
     loss.backward()
@@ -194,10 +195,20 @@ def _run_case(model, x, y, lr):
     return logit_eval, logit_train, loss, g, logit_after, model.state_dict()
 
 
-def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma=0.25, fc_gain=8.0):
+def _seed_train(train_seed):
+    """MixStyle cases: seed both generators the reference's MixStyle draws from right before the train forward (model construction
+    consumes the torch generator)."""
+    if train_seed is not None:
+        random.seed(train_seed)
+        torch.manual_seed(train_seed)
+
+
+def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma=0.25, fc_gain=8.0, make=None, train_seed=None, extra=None):
+    """make: the reference model constructor (default: its plain ResNet); train_seed: see _seed_train."""
     if not wanted(name):
         return
-    model = ref_resnet.ResNet(block, layers, classes=classes)
+    make = make or (lambda: ref_resnet.ResNet(block, layers, classes=classes))
+    model = make()
     ours = R.ResNet(block, layers, classes=classes)
     # conditioned like a trained net (small closing-BN gammas), see oracle.resnet_ref.seeded_state_dict
     sd = R.seeded_state_dict(ours, seed, residual_gamma=residual_gamma, fc_gain=fc_gain)
@@ -209,6 +220,7 @@ def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma
     model.train()
     opt = torch.optim.SGD(model.parameters(), lr=lr)         # fed_run.py:657 form, README.md:99 lr
     opt.zero_grad()
+    _seed_train(train_seed)
     logit_train = model(x)
     loss = nn.CrossEntropyLoss()(logit_train, y)               # fed_run.py:554
     loss.backward()
@@ -230,10 +242,10 @@ def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma
         probe["state/" + k] = sd_after[k]
     # conditioning of the problem: the SAME reference model in float64.  |fp32 - fp64| per probe is the
     # noise floor any fp32 implementation sits on (tiny batch + train-mode BN + ReLU/max-pool masks).
-    m64 = ref_resnet.ResNet(block, layers, classes=classes)
+    m64 = make()
     m64.load_state_dict(sd)
     m64 = m64.double()
-    le64, lt64, loss64, g64, la64, _ = _run_case(m64, x.double(), y, lr)
+    le64, lt64, loss64, g64, la64, _ = _run_case(m64, x.double(), y, lr, train_seed)
     probe["noise/logit_eval"] = (logit_eval.double() - le64).abs().max()
     probe["noise/logit_train"] = (logit_train.double() - lt64).abs().max()
     probe["noise/logit_after"] = (logit_after.double() - la64).abs().max()
@@ -247,11 +259,139 @@ def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma
             # worst fp32 error over the WHOLE gradient tensor (same conditioning, far steadier estimate)
             probe["noise_full/grad/" + n_] = (g[n_].double() - g64[n_]).abs().max()
     save(name, seed=seed, classes=classes, nb=nb, lr=lr, residual_gamma=residual_gamma, fc_gain=fc_gain, logit_eval=logit_eval, logit_train=logit_train,
-         loss=loss, logit_after=logit_after, **probe)
+         loss=loss, logit_after=logit_after, **probe, **(extra or {}))
 
 
 resnet_case("resnet18_step", R.BasicBlock, [2, 2, 2, 2], 2, 8, seed=50)
 resnet_case("resnet50_step", R.Bottleneck, [3, 4, 6, 3], 7, 16, seed=60)
+
+# --------------------------------------------------------------------------
+# MixStyle (nets/layers.py:6-73, MixStyleResNet nets/resnet.py:281-311)
+# --------------------------------------------------------------------------
+import random  # noqa: E402
+from nets import layers as ref_layers   # noqa: E402  (reference module)
+
+
+def mixstyle_input(shape, seed):
+    """Per-(image, channel) means in [-1, 1] and sigmas in [0.5, 2]: sigma stays far above sqrt(eps).  Upstream gradient: N(0, 1)."""
+    rs = np.random.RandomState(seed)
+    N, C, H, W = shape
+    mu = rs.uniform(-1.0, 1.0, (N, C, 1, 1))
+    sd = rs.uniform(0.5, 2.0, (N, C, 1, 1))
+    x = (mu + sd * rs.standard_normal(shape)).astype(np.float32)
+    g = rs.standard_normal(shape).astype(np.float32)
+    return torch.from_numpy(x), torch.from_numpy(g)
+
+
+class _DrawSpy(object):
+    """Records what the reference's MixStyle draws (random.random, Beta.sample, torch.randperm) while calling the originals."""
+
+    def __init__(self, ms):
+        self.ms, self.gate, self.lmda, self.rps = ms, [], [], []
+
+    def __enter__(self):
+        self.rr, self.rp, self.bs = random.random, torch.randperm, self.ms.beta.sample
+
+        def rr():
+            v = self.rr()
+            self.gate.append(v)
+            return v
+
+        def rp(*a, **k):
+            v = self.rp(*a, **k)
+            self.rps.append(v.clone())
+            return v
+
+        def bs(*a, **k):
+            v = self.bs(*a, **k)
+            self.lmda.append(v.clone())
+            return v
+        ref_layers.random.random, ref_layers.torch.randperm, self.ms.beta.sample = rr, rp, bs
+        return self
+
+    def __exit__(self, *exc):
+        ref_layers.random.random, ref_layers.torch.randperm = self.rr, self.rp
+        del self.ms.beta.sample
+        return False
+
+
+def mixstyle_perm(mix, B, rps):
+    """The permutation the reference forms from its randperm draws (nets/layers.py:56-66)."""
+    if mix == "random":
+        return rps[0]
+    rev = torch.arange(B - 1, -1, -1)
+    return torch.cat([rev[:B // 2][rps[0]], rev[B // 2:][rps[1]]], 0)
+
+
+def mixstyle_call(ms, x, g):
+    """One training forward + backward of the reference module; returns its draws and results (lambda / perm zero when the gate is shut)."""
+    xx = x.clone().requires_grad_(True)
+    with _DrawSpy(ms) as spy:
+        y = ms(xx)
+    y.backward(g)
+    B = x.shape[0]
+    fired = len(spy.lmda) == 1
+    lmda = spy.lmda[0].reshape(B) if fired else torch.zeros(B)
+    perm = mixstyle_perm(ms.mix, B, spy.rps) if fired else torch.zeros(B, dtype=torch.int64)
+    return dict(gate=spy.gate[0], fired=fired, lmda=lmda, perm=perm, y=y.detach(), dx=xx.grad)
+
+
+if wanted("mixstyle_module"):
+    import warnings
+    out = {}
+    cases = [("a", (8, 64, 6, 6), 301), ("b", (6, 96, 5, 9), 302), ("hw1", (4, 20, 1, 1), 303)]
+    names = []
+    for tag, shape, seed in cases:
+        x, g = mixstyle_input(shape, seed)
+        for mix in ("random", "crossdomain"):
+            name = "%s_%s" % (tag, mix)
+            names.append(name)
+            ms = ref_layers.MixStyle(p=1.0, mix=mix).train()
+            random.seed(seed)
+            torch.manual_seed(seed)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")          # (HW = 1: var() of one element warns, and is NaN)
+                r = mixstyle_call(ms, x, g)
+            assert r["fired"]
+            out.update({name + "/" + k: v for k, v in r.items()})
+            out[name + "/shape"], out[name + "/seed"] = list(shape), seed
+            out[name + "/probe_random"], out[name + "/probe_torch"] = random.random(), torch.rand(4)
+    # p = 0.5: consecutive calls of one module from one seed (seed chosen so that the gate both fires and stays shut)
+    seq_shape, seq_seed, K = (4, 16, 5, 5), 310, 6
+    ms = ref_layers.MixStyle(p=0.5, mix="random").train()
+    random.seed(seq_seed)
+    torch.manual_seed(seq_seed)
+    seq = []
+    for k in range(K):
+        x, g = mixstyle_input(seq_shape, seq_seed + 1 + k)
+        seq.append(mixstyle_call(ms, x, g))
+    fired = [r["fired"] for r in seq]
+    assert any(fired) and not all(fired), fired
+    for k_ in ("gate", "fired", "lmda", "perm", "y", "dx"):
+        out["seq/" + k_] = [r[k_] for r in seq] if k_ in ("gate", "fired") else torch.stack([r[k_] for r in seq])
+    out["seq/shape"], out["seq/seed"], out["seq/K"] = list(seq_shape), seq_seed, K
+    out["seq/probe_random"], out["seq/probe_torch"] = random.random(), torch.rand(4)
+    out["repr"] = repr(ref_layers.MixStyle())
+    save("mixstyle_module", cases=np.array(names), **out)
+
+
+def mixstyle_gates(seed, n=3):
+    random.seed(seed)
+    return [random.random() for _ in range(n)]
+
+
+def mixstyle_resnet_case(name, block, layers, classes, nb, seed, p):
+    # (each site's gate is one random.random(); the seed search keeps the sites mixed at p = 0.5)
+    train_seed = next(s for s in range(1000 + seed, 2000 + seed)
+                      if p >= 1.0 or len({v > p for v in mixstyle_gates(s)}) == 2)
+    make = (lambda: ref_resnet.MixStyleResNet(block, layers, classes=classes, mixstyle_layers=["layer1", "layer2", "layer3"], mixstyle_p=p))
+    resnet_case(name, block, layers, classes, nb, seed, make=make, train_seed=train_seed,
+                extra={"train_seed": train_seed, "mixstyle_p": p, "gates": mixstyle_gates(train_seed)})
+
+
+mixstyle_resnet_case("mixstyle_resnet18_step", R.BasicBlock, [2, 2, 2, 2], 2, 8, seed=50, p=0.5)
+mixstyle_resnet_case("mixstyle_resnet18_p1_step", R.BasicBlock, [2, 2, 2, 2], 2, 8, seed=52, p=1.0)
+mixstyle_resnet_case("mixstyle_resnet50_step", R.Bottleneck, [3, 4, 6, 3], 7, 16, seed=60, p=0.5)
 
 # communication() on 3 perturbed clients (fed_run.py:385-455, fedavg branch)
 nsf = {"torch": torch, "nn": nn}
