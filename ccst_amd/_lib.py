@@ -176,6 +176,33 @@ def load_mixstyle():
     return lib
 
 
+# The instance-norm extension ABI (include/ccst_instnorm.h), bound the same way.
+INSTNORM_ABI_VERSION = 1
+_INSTNORM_SIGNATURES = {
+    "ccst_instnorm_abi_version": [],
+    "ccst_instnorm_workspace_bytes": [c_int, c_int, c_int],
+    "ccst_instnorm_fwd_f32": [_P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, c_int64, _P, _P],
+    "ccst_instnorm_bwd_f32": [_P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P],
+}
+INSTNORM_EXPORTS = tuple(_INSTNORM_SIGNATURES)
+_instnorm_bound = False
+
+
+def load_instnorm():
+    """load() with the instance-norm entry points bound; raise if the library's extension version is not INSTNORM_ABI_VERSION."""
+    global _instnorm_bound
+    lib = load()
+    if not _instnorm_bound:
+        for name, argtypes in _INSTNORM_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int64 if name == "ccst_instnorm_workspace_bytes" else c_int
+        if lib.ccst_instnorm_abi_version() != INSTNORM_ABI_VERSION:
+            raise RuntimeError("ccst_amd: instance-norm extension ABI version mismatch")
+        _instnorm_bound = True
+    return lib
+
+
 def check(rc, what):
     if rc != 0:
         msg = load().ccst_last_error()

@@ -411,11 +411,40 @@ def train(model, train_loader, optimizer, loss_fun, client_num, device, args, it
     return train_loss, train_acc
 
 
+def _set_module(model, key, module):
+    tokens = key.split('.')
+    cur = model
+    for t in tokens[:-1]:
+        cur = getattr(cur, t)
+    setattr(cur, tokens[-1], module)
+
+
+def swap_bn_for_in(model, device):
+    """fed_run.py:218-229 (--IN_test): every nn.BatchNorm2d of the model is replaced, in place, by an affine InstanceNorm2d (the fused
+    drop-in of nets/resnet.py) with the same num_features, eps and momentum, taking over the BatchNorm's weight and bias.  The model
+    stays swapped: its state dict loses the running statistics, a second call finds nothing to swap.  The parameter arena, the
+    captured train steps and the counter arena held the replaced tensors: they are dropped, to be rebuilt from the live modules."""
+    from .nets.resnet import InstanceNorm2d
+    swapped = False
+    for name, m in list(model.named_modules()):
+        if isinstance(m, nn.BatchNorm2d):
+            IN = InstanceNorm2d(m.num_features, eps=m.eps, momentum=m.momentum, affine=True).to(device)
+            with torch.no_grad():
+                IN.weight.copy_(m.weight)
+                IN.bias.copy_(m.bias)
+            _set_module(model, name, IN)
+            swapped = True
+    if swapped:
+        for k in ("_ccst_arena", "_ccst_graph_steps", "_ccst_nbt"):
+            model.__dict__.pop(k, None)
+    return swapped
+
+
 def test(model, test_loader, loss_fun, device, args):
-    if getattr(args, "IN_test", False):
-        raise NotImplementedError("ccst_amd.fed: --IN_test is outside the hot path")
     model.to(device)
     model.eval()
+    if getattr(args, "IN_test", False):
+        swap_bn_for_in(model, device)
     num_data = 0
     loss_all = torch.zeros((), device=device)
     correct_all = torch.zeros((), device=device, dtype=torch.int64)
@@ -458,6 +487,35 @@ def _copy_counters(server_model, client0):
             ssd[key].data.copy_(c0[key])
 
 
+def _key_layout(model):
+    return [(k, tuple(v.shape), v.dtype) for k, v in model.state_dict().items()]
+
+
+def _communication_by_key(mode, server_model, models, client_weights):
+    """communication() when the server's state-dict keys are not the clients' (a server swapped by --IN_test, fed_run.py:218-229, has
+    no running statistics while its BatchNorm clients still have them): the reference's key loop over the SERVER's keys
+    (fed_run.py:388-414) -- 'num_batches_tracked' from client 0, every other entry the weighted sum of the clients' entries under that
+    key, copied back to the clients (fedbn: the keys without 'bn' only).  Client entries the server lacks stay as they are.  Each sum
+    runs on the arenas' fp32 slices with the axpy launches of the flat path (communication() has built the arenas and joined the
+    side-stream re-packs)."""
+    ssd = server_model.state_dict()
+    csd = [m.state_dict() for m in models]
+    for key, v in ssd.items():
+        if 'num_batches_tracked' in key:
+            continue
+        if any(key not in c or tuple(c[key].shape) != tuple(v.shape) for c in csd[:len(client_weights)]):
+            raise KeyError("communication: client models lack the server's entry %r" % key)
+        nn_ops.fill_(v, 0.0)
+        for ci in range(len(client_weights)):
+            _axpy(v, csd[ci][key], client_weights[ci])
+        if mode != "fedbn" or 'bn' not in key:
+            for ci in range(len(client_weights)):
+                csd[ci][key].copy_(v)
+    ops.bump_weights_epoch()
+    _copy_counters(server_model, models[0])
+    return server_model, models
+
+
 def communication(args, server_model, models, client_weights):
     """fed_run.py:385-455, the branch every non-'fedbn' mode takes (:400-414): for each state key,
     'num_batches_tracked' -> server takes client 0's value (clients keep theirs); otherwise
@@ -474,6 +532,8 @@ def communication(args, server_model, models, client_weights):
         nn_ops.join_prepack(arenas[0].flat.device)      # side-stream re-packs still read the client weights
         srv, clients = arenas[0], arenas[1:]
         if any(c.n_total != srv.n_total for c in clients):
+            if all(_key_layout(m) == _key_layout(models[0]) for m in models) and _key_layout(server_model) != _key_layout(models[0]):
+                return _communication_by_key(mode, server_model, models, client_weights)
             raise ValueError("communication: client and server models differ in size")
         K = len(client_weights)
         fused = mode != "fedbn" and 1 <= K <= 16 and len({c.flat.data_ptr() for c in clients[:K]} | {srv.flat.data_ptr()}) == K + 1

@@ -5,13 +5,13 @@ from . import resnet
 def _out_of_scope(name):
     def ctor(*a, **k):
         raise NotImplementedError("ccst_amd.nets: '%s' is outside the hot path this library implements "
-                                  "(SURVEY.md section 2: only resnet18 / resnet50 are on it)" % name)
+                                  "(SURVEY.md section 2: only resnet18 / resnet18IN / resnet50 are on it)" % name)
     return ctor
 
 
 nets_map = {
     'resnet18': resnet.resnet18,
-    'resnet18IN': _out_of_scope('resnet18IN'),
+    'resnet18IN': resnet.resnet18IN,
     'resnet50': resnet.resnet50,
     'DigitModel': _out_of_scope('DigitModel'),
     'densenet': _out_of_scope('densenet'),

@@ -120,10 +120,12 @@ class Conv2d(nn.Conv2d):
             return ops.pack_conv_weight(wv), kwp
         return self._cached("pks", build)
 
-    def forward(self, x, want_stats=False, sink=None, sole_reader=False):
+    def forward(self, x, want_stats=False, sink=None, sole_reader=False, grad_words=False):
         """want_stats=True (training only): returns (y, stats) with the BatchNorm batch-statistic partials of y
         produced in the conv epilogue; pass them to the following BatchNorm2d(..., stats=stats).
-        sink: nn_ops.GradSink whose content this conv's backward-data adds to (residual blocks)."""
+        sink: nn_ops.GradSink whose content this conv's backward-data adds to (residual blocks).
+        grad_words=True (no statistics: an InstanceNorm2d reads y): y carries the GradWords holder through which that norm's
+        backward hands the |max| words of y's gradient to this conv's backward, as with want_stats."""
         self._check()
         if not x.is_cuda:
             raise RuntimeError("ccst_amd.nets: CUDA (ROCm) tensors only; no CPU fallback")
@@ -150,6 +152,11 @@ class Conv2d(nn.Conv2d):
             out = ops.to_api(y)
             out._ccst_gw = gw
             return out, stats
+        if grad_words and self.training and torch.is_grad_enabled():
+            gw = nn_ops.GradWords()
+            out = ops.to_api(nn_ops.ConvFn.apply(ops.carry_absmax(x, _to_nhwc(x)), self.weight, self, False, sink, link, gw))
+            out._ccst_gw = gw
+            return out
         return ops.to_api(nn_ops.ConvFn.apply(ops.carry_absmax(x, _to_nhwc(x)), self.weight, self, False, sink, link))
 
 
@@ -171,10 +178,34 @@ class BatchNorm2d(nn.BatchNorm2d):
         return out
 
 
+class InstanceNorm2d(nn.InstanceNorm2d):
+    """InstanceNorm2d (instance statistics in training and evaluation) fused with an optional residual add and ReLU, with the
+    BatchNorm2d call shape: y = relu(in(x) + residual).  Not a BatchNorm2d: the fused BatchNorm stem and the gradient short-cuts
+    between blocks (MaskLink, GradSink) stay off wherever it is the norm."""
+
+    def forward(self, x, residual=None, relu=False, stats=None, sink=None):
+        if stats is not None or sink is not None:
+            raise NotImplementedError("ccst_amd.nets: InstanceNorm2d takes no conv statistics or gradient sink")
+        if not x.is_cuda:
+            raise RuntimeError("ccst_amd.nets: CUDA (ROCm) tensors only; no CPU fallback")
+        if self.track_running_stats:
+            raise NotImplementedError("ccst_amd.nets: InstanceNorm2d with running statistics is not on the reference path")
+        res = _to_nhwc(residual) if residual is not None else None
+        if not torch.is_grad_enabled():         # (evaluation: nothing to save for a backward)
+            y = ops.instnorm_fwd(_to_nhwc(x), self.weight, self.bias, res, bool(relu), float(self.eps), want_words=nn_ops.HALF_FWD)[0]
+            return ops.carry_absmax(y, ops.to_api(y))
+        gw = getattr(x, "_ccst_gw", None) if self.training else None
+        y = nn_ops.InstanceNormFn.apply(_to_nhwc(x), self.weight, self.bias, res, bool(relu), float(self.eps), gw)
+        return ops.carry_absmax(y, ops.to_api(y))
+
+
 def conv_bn(conv, bn, x, residual=None, relu=False, sink_in=None, sink_out=None, sole_reader=False):
     """bn(conv(x)) [+ residual] [ReLU]; in training the batch statistics come out of the conv epilogue.
     sink_out / sink_in: the GradSink that this BatchNorm's backward fills with the residual gradient / that this
-    conv's backward-data adds to (a residual block whose identity branch is its input, see _residual_sink)."""
+    conv's backward-data adds to (a residual block whose identity branch is its input, see _residual_sink).
+    An InstanceNorm2d takes its statistics itself: the conv runs without the epilogue and hands it the gradient-words holder."""
+    if isinstance(bn, InstanceNorm2d):
+        return bn(conv(x, sink=sink_in, sole_reader=sole_reader, grad_words=True), residual=residual, relu=relu)
     if bn.training:
         y, stats = conv(x, want_stats=True, sink=sink_in, sole_reader=sole_reader)
         return bn(y, residual=residual, relu=relu, stats=stats, sink=sink_out)
@@ -193,9 +224,14 @@ def _plain_reader(x):
     return not (x.retains_grad or x._backward_hooks)
 
 
+def _batch_norm_block(block):
+    """Are the block's norms the BatchNorm2d the gradient short-cuts are built for (not an InstanceNorm2d block)?"""
+    return isinstance(block.bn1, BatchNorm2d)
+
+
 def _pair_sink(block, x):
     """The GradSink shared by the two convolutions that read x in a block with a downsample branch (see nn_ops.GradSink)."""
-    if USE_GRAD_SINK and block.downsample is not None and block.training and torch.is_grad_enabled() and x.requires_grad \
+    if USE_GRAD_SINK and _batch_norm_block(block) and block.downsample is not None and block.training and torch.is_grad_enabled() and x.requires_grad \
             and _plain_reader(x):
         return nn_ops.GradSink(pair=True)
     return None
@@ -204,7 +240,7 @@ def _pair_sink(block, x):
 def _residual_sink(block, x, first_conv):
     """A GradSink when the block's identity branch is x itself, x needs a gradient and the first conv has stride 1
     (then d(identity) and the first conv's dX have the same shape and the conv can add to it in place)."""
-    if USE_GRAD_SINK and block.downsample is None and block.training and torch.is_grad_enabled() and x.requires_grad \
+    if USE_GRAD_SINK and _batch_norm_block(block) and block.downsample is None and block.training and torch.is_grad_enabled() and x.requires_grad \
             and first_conv.stride[0] == 1 and _plain_reader(x):
         return nn_ops.GradSink()
     return None
@@ -254,16 +290,31 @@ def conv1x1(in_planes, out_planes, stride=1):
     return Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
 
 
+def _norm_layer(norm_layer):
+    """torchvision's norm_layer keyword: None is this module's BatchNorm2d; nn.InstanceNorm2d (nets/resnet.py:225,228) is its fused
+    InstanceNorm2d."""
+    if norm_layer is None or norm_layer is BatchNorm2d:
+        return BatchNorm2d
+    if norm_layer is nn.InstanceNorm2d or norm_layer is InstanceNorm2d:
+        return InstanceNorm2d
+    raise NotImplementedError("ccst_amd.nets: norm_layer %r (BatchNorm2d or InstanceNorm2d only)" % (norm_layer,))
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1, norm_layer=None):
         super().__init__()
+        norm_layer = _norm_layer(norm_layer)
+        if groups != 1 or base_width != 64:
+            raise ValueError('BasicBlock only supports groups=1 and base_width=64')
+        if dilation > 1:
+            raise NotImplementedError("Dilation > 1 not supported in BasicBlock")
         self.conv1 = conv3x3(inplanes, planes, stride)
-        self.bn1 = BatchNorm2d(planes)
+        self.bn1 = norm_layer(planes)
         self.relu = ReLU(inplace=True)
         self.conv2 = conv3x3(planes, planes)
-        self.bn2 = BatchNorm2d(planes)
+        self.bn2 = norm_layer(planes)
         self.downsample = downsample
         self.stride = stride
 
@@ -282,14 +333,17 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1, norm_layer=None):
         super().__init__()
+        norm_layer = _norm_layer(norm_layer)
+        if groups != 1 or base_width != 64 or dilation != 1:
+            raise NotImplementedError("ccst_amd.nets: Bottleneck with groups=1, base_width=64 and dilation=1 only (the reference's ResNets)")
         self.conv1 = conv1x1(inplanes, planes)
-        self.bn1 = BatchNorm2d(planes)
+        self.bn1 = norm_layer(planes)
         self.conv2 = conv3x3(planes, planes, stride)
-        self.bn2 = BatchNorm2d(planes)
+        self.bn2 = norm_layer(planes)
         self.conv3 = conv1x1(planes, planes * self.expansion)
-        self.bn3 = BatchNorm2d(planes * self.expansion)
+        self.bn3 = norm_layer(planes * self.expansion)
         self.relu = ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -445,6 +499,53 @@ class MixStyleResNet(ResNet):
         x = self.avgpool(x)
         x = x.view(x.size(0), -1)
         return self.class_classifier(x)
+
+
+class ResNetIN(ResNet):
+    """nets/resnet.py:193-232: the ResNet with InstanceNorm2d.  As in the reference, the base constructor first builds a complete
+    ResNet (consuming the generator), then conv1, bn1 (an affine InstanceNorm2d), relu, maxpool, layer1..4 (blocks and downsample
+    branches with non-affine InstanceNorm2d), avgpool and class_classifier are built again and the kaiming loop runs again -- so
+    equal seeds give the reference's initial weights and state-dict keys.  Only bn1 carries norm state (weight, bias); nothing
+    tracks running statistics.  Stem: conv1 -> InstanceNorm + ReLU -> MaxPool2d."""
+
+    def __init__(self, block, layers, classes=100):
+        super(ResNetIN, self).__init__(block=block, layers=layers, classes=classes)
+        self.inplanes = 64
+        self.conv1 = Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = InstanceNorm2d(64, affine=True)
+        self.relu = ReLU(inplace=True)
+        self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        self.avgpool = AvgPool2d(7, stride=1)
+        self.class_classifier = Linear(512 * block.expansion, classes)
+
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def _make_layer(self, block, planes, blocks, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(
+                Conv2d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, bias=False),
+                InstanceNorm2d(planes * block.expansion),
+            )
+        layers = [block(self.inplanes, planes, stride, downsample, norm_layer=InstanceNorm2d)]
+        self.inplanes = planes * block.expansion
+        for _ in range(1, blocks):
+            layers.append(block(self.inplanes, planes, norm_layer=InstanceNorm2d))
+        return nn.Sequential(*layers)
+
+
+def resnet18IN(args, pretrained=False, **kwargs):
+    """nets/resnet.py:347-348: ResNetIN with BasicBlock [2, 2, 2, 2].  Like the reference it ignores args (dg_method) and pretrained."""
+    return ResNetIN(BasicBlock, [2, 2, 2, 2], **kwargs)
 
 
 def _unsupported(args):

@@ -875,3 +875,32 @@ class MixStyleFn(torch.autograd.Function):
     def backward(ctx, dy):
         stat, draws = ctx.saved_tensors
         return ops.mixstyle_bwd(dy, stat, draws), None, None
+
+
+class InstanceNormFn(torch.autograd.Function):
+    """InstanceNorm2d (track_running_stats=False: instance statistics in training and evaluation) fused with an optional residual add
+    and ReLU on NHWC: y = relu(instance_norm(x) [gamma + beta] + residual).  gamma = beta = None: the non-affine norm.  y carries its
+    |max| words for a half-piece pointwise conv that reads it; the backward leaves max |dx| in `gw` (the GradWords of the conv that
+    produced x).  No MaskLink or GradSink crosses it: the backward applies its own ReLU mask -- the forward's byte mask after a
+    residual, recomputed from x without one -- and returns the skip connection's share to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, relu, eps, gw=None):
+        ctx.gw = gw
+        ctx.relu, ctx.has_res = bool(relu), residual is not None
+        grad = any(ctx.needs_input_grad)
+        y, save, mask = ops.instnorm_fwd(x, gamma, beta, residual, relu, eps, want_mask=grad and ctx.has_res, want_words=HALF_FWD)
+        if grad:
+            ctx.save_for_backward(x, mask, gamma, beta, save)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mask, gamma, beta, save = ctx.saved_tensors
+        dxmax = _publish_grad_words(x.device, ctx.gw)
+        dx, dres = ops.instnorm_bwd(dy, x, save, gamma, beta, ctx.relu, mask=mask, want_dres=ctx.has_res and ctx.needs_input_grad[3],
+                                    dgamma=_grad_slot(gamma) if gamma is not None else None,
+                                    dbeta=_grad_slot(beta) if beta is not None else None, dx_words=dxmax)
+        if dxmax is not None:
+            ctx.gw.put(dx, dxmax)
+        return dx, None, None, dres, None, None, None

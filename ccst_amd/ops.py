@@ -1111,3 +1111,52 @@ def mixstyle_bwd(dy, stat, draws):
     check(_lib.load_mixstyle().ccst_mixstyle_bwd_f32(ptr(dy), ptr(stat[1]), ptr(draws[:N]), ptr(draws[N:]), ptr(dx), N, C, H * W, stream_ptr()),
           "mixstyle_bwd")
     return dx
+
+
+# ---------------------------------------------------------------------------
+# Instance normalisation (include/ccst_instnorm.h)
+# ---------------------------------------------------------------------------
+def _instnorm_ws(N, HW, C, device):
+    from .nn_ops import _workspace
+    nb = int(_lib.load_instnorm().ccst_instnorm_workspace_bytes(N, HW, C))
+    return _workspace(nb, device), nb
+
+
+def instnorm_fwd(x, gamma=None, beta=None, residual=None, relu=False, eps=1e-5, want_mask=False, want_words=True):
+    """y = [ReLU]((x - mu) invstd [gamma + beta] [+ residual]) over each (image, channel) of an NHWC-contiguous [N,H,W,C] CUDA tensor,
+    mu and the biased variance over H x W (F.instance_norm).  Returns (y tagged with its |max| words when want_words, save [2, N*C] =
+    mean | invstd, the byte ReLU mask or None)."""
+    _require_cuda(x, "input")
+    N, H, W, C = x.shape
+    if C % 4 != 0 or not x.is_contiguous():
+        raise RuntimeError("ccst_amd: InstanceNorm needs an NHWC-contiguous tensor with C %% 4 == 0 (C=%d)" % C)
+    if (gamma is None) != (beta is None):
+        raise ValueError("ccst_amd: InstanceNorm takes gamma and beta together (affine) or neither")
+    if residual is not None and (tuple(residual.shape) != tuple(x.shape) or not residual.is_contiguous()):
+        raise RuntimeError("ccst_amd: the InstanceNorm residual must be an NHWC-contiguous tensor of the input's shape")
+    y = torch.empty_like(x)
+    save = torch.empty((2, N * C), device=x.device, dtype=torch.float32)
+    mask = torch.empty((x.numel() // 4,), device=x.device, dtype=torch.uint8) if (want_mask and relu) else None
+    ws, nb = _instnorm_ws(N, H * W, C, x.device)
+    words = absmax_words(x.device) if want_words else None
+    check(_lib.load_instnorm().ccst_instnorm_fwd_f32(ptr(x), ptr(gamma), ptr(beta), ptr(residual), int(bool(relu)), ptr(y), ptr(mask),
+                                                     ptr(save[0]), ptr(save[1]), N, H * W, C, float(eps), ptr(ws), nb, ptr(words),
+                                                     stream_ptr()), "instnorm_fwd")
+    if words is not None:
+        tag_absmax(y, words)
+    return y, save, mask
+
+
+def instnorm_bwd(dy, x, save, gamma=None, beta=None, relu=False, y=None, mask=None, want_dres=False, dgamma=None, dbeta=None,
+                 accumulate=True, dx_words=None):
+    """Backward of instnorm_fwd: returns (dx, d_residual or None).  dgamma / dbeta: tensors the parameter gradients are written to
+    (added to with accumulate); dx_words: zeroed |max| words receiving max |dx|, or None."""
+    dy = dy.contiguous()
+    N, H, W, C = x.shape
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    ws, nb = _instnorm_ws(N, H * W, C, x.device)
+    check(_lib.load_instnorm().ccst_instnorm_bwd_f32(ptr(dy), ptr(x), ptr(y), ptr(mask), int(bool(relu)), ptr(gamma), ptr(beta), ptr(save[0]),
+                                                     ptr(save[1]), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), int(bool(accumulate)), N, H * W,
+                                                     C, ptr(ws), nb, ptr(dx_words), stream_ptr()), "instnorm_bwd")
+    return dx, dres

@@ -12,6 +12,8 @@ Two launch forms
 --mode fedbn (fed_run.py:388-399, :693-698, :735-759): clients keep every state entry whose key contains 'bn',
 are validated with their local model, and checkpoints also carry 'model_{k}' state dicts.
 --dg_method MixStyle (nets/resnet.py:281-311): MixStyle after layer1..3 of the ResNet, trained eagerly (never HIP-graph captured).
+--network resnet18IN (nets/resnet.py:193-232): the ResNet18 with InstanceNorm2d.  --IN_test (fed_run.py:218-229): test() evaluates
+with every BatchNorm2d replaced by an affine InstanceNorm2d that takes over its weight and bias (the model stays swapped).
 Out of scope: adafea / fedprox aggregation variants, RSC / Jigsaw /
 FedDG, Tent, tensorboard / Excel logging."""
 import argparse
@@ -108,6 +110,9 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ccst_amd: an MI355X (ROCm) device is required; there is no CPU path")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.IN_test and world > 1 and not args.test:
+        # (the validation / test passes of a round would swap this rank's client model, which the one-process schedule never tests)
+        raise SystemExit("--IN_test while training runs as one process (or use it with --test)")
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
     torch.cuda.set_device(local)

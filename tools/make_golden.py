@@ -203,13 +203,22 @@ def _seed_train(train_seed):
         torch.manual_seed(train_seed)
 
 
-def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma=0.25, fc_gain=8.0, make=None, train_seed=None, extra=None):
-    """make: the reference model constructor (default: its plain ResNet); train_seed: see _seed_train."""
+GRAD_PROBES = ["conv1.weight", "bn1.weight", "bn1.bias", "class_classifier.weight", "class_classifier.bias", "layer1.0.conv1.weight",
+               "layer2.0.downsample.0.weight", "layer4.%d.conv2.weight", "layer3.0.bn2.weight"]
+STATE_PROBES = ["bn1.running_mean", "bn1.running_var", "layer4.0.bn1.running_mean", "layer2.0.downsample.1.running_var", "bn1.num_batches_tracked"]
+
+
+def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma=0.25, fc_gain=8.0, make=None, train_seed=None, extra=None,
+                grad_probes=GRAD_PROBES, state_probes=STATE_PROBES):
+    """make: the reference model constructor (default: its plain ResNet); train_seed: see _seed_train.  The seeded state is drawn over
+    the state-dict keys of the oracle's ResNet, or of the model itself when their keys differ (the InstanceNorm ResNet)."""
     if not wanted(name):
         return
     make = make or (lambda: ref_resnet.ResNet(block, layers, classes=classes))
     model = make()
     ours = R.ResNet(block, layers, classes=classes)
+    if list(ours.state_dict()) != list(model.state_dict()):
+        ours = model
     # conditioned like a trained net (small closing-BN gammas), see oracle.resnet_ref.seeded_state_dict
     sd = R.seeded_state_dict(ours, seed, residual_gamma=residual_gamma, fc_gain=fc_gain)
     model.load_state_dict(sd)
@@ -231,14 +240,12 @@ def resnet_case(name, block, layers, classes, nb, seed, lr=0.001, residual_gamma
         logit_after = model(x)
     sd_after = model.state_dict()
     probe = {}
-    for k in ["conv1.weight", "bn1.weight", "bn1.bias", "class_classifier.weight", "class_classifier.bias",
-              "layer1.0.conv1.weight", "layer2.0.downsample.0.weight", "layer4.%d.conv2.weight" % (layers[3] - 1),
-              "layer3.0.bn2.weight"]:
+    for k in grad_probes:
+        k = k % (layers[3] - 1) if "%d" in k else k
         probe["grad_sum/" + k] = g[k].sum()
         probe["grad_abs/" + k] = g[k].abs().sum()
         probe["grad_head/" + k] = g[k].flatten()[:16]
-    for k in ["bn1.running_mean", "bn1.running_var", "layer4.0.bn1.running_mean", "layer2.0.downsample.1.running_var",
-              "bn1.num_batches_tracked"]:
+    for k in state_probes:
         probe["state/" + k] = sd_after[k]
     # conditioning of the problem: the SAME reference model in float64.  |fp32 - fp64| per probe is the
     # noise floor any fp32 implementation sits on (tiny batch + train-mode BN + ReLU/max-pool masks).
@@ -491,6 +498,126 @@ save("fed_loop", seed=91, train_seeds=[100, 101, 102], train_sizes=[4, 4, 3], te
      l4_bn2_weight=lsd["layer4.0.bn2.weight"], nbt=int(lsd["bn1.num_batches_tracked"]),
      key_sum=np.array([float(v.double().sum()) for v in lsd.values()]),
      key_abs=np.array([float(v.double().abs().sum()) for v in lsd.values()]))
+# --------------------------------------------------------------------------
+# The InstanceNorm ResNet (ResNetIN, nets/resnet.py:193-232) and --IN_test (fed_run.py:218-229)
+# --------------------------------------------------------------------------
+class INBasicBlock(nn.Module):
+    """torchvision's v1.5 BasicBlock restated WITH its norm_layer keyword, which the reference's ResNetIN passes nn.InstanceNorm2d
+    through (the oracle's restated blocks take none).  Same modules in the same order: the same generator draws."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1, norm_layer=None):
+        super().__init__()
+        if norm_layer is None:
+            norm_layer = nn.BatchNorm2d
+        if groups != 1 or base_width != 64:
+            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
+        if dilation > 1:
+            raise NotImplementedError("Dilation > 1 not supported in BasicBlock")
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
+        self.bn1 = norm_layer(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = norm_layer(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        out += identity
+        return self.relu(out)
+
+
+def ref_resnet18IN(classes):
+    """The reference's resnet18IN (nets/resnet.py:347-348) with the block that takes norm_layer."""
+    saved = ref_resnet.BasicBlock
+    ref_resnet.BasicBlock = INBasicBlock
+    try:
+        return ref_resnet.resnet18IN(types.SimpleNamespace(dg_method="no_DG"), pretrained=False, classes=classes)
+    finally:
+        ref_resnet.BasicBlock = saved
+
+
+def key_stats(sd):
+    keys = list(sd.keys())
+    return (np.array(keys), np.array([float(sd[k].double().sum()) for k in keys]), np.array([float(sd[k].double().abs().sum()) for k in keys]))
+
+
+if wanted("resnet18in_init"):
+    out = {}
+    for seed in (0, 1):
+        torch.manual_seed(seed)
+        m = ref_resnet18IN(7)
+        keys, ksum, kabs = key_stats(m.state_dict())
+        out.update({"keys": keys, "key_sum_%d" % seed: ksum, "key_abs_%d" % seed: kabs})
+    # (the stub block restates torchvision's BasicBlock: recorded under that name)
+    mods = [(n, "BasicBlock" if type(mm) is INBasicBlock else type(mm).__name__) for n, mm in m.named_modules()]
+    norms = [(n, bool(mm.affine), bool(mm.track_running_stats)) for n, mm in m.named_modules() if isinstance(mm, nn.InstanceNorm2d)]
+    save("resnet18in_init", seeds=[0, 1], classes=7, module_names=np.array([n for n, _ in mods]), module_types=np.array([t for _, t in mods]),
+         norm_names=np.array([n for n, _, _ in norms]), norm_affine=np.array([a for _, a, _ in norms]),
+         norm_track=np.array([t for _, _, t in norms]), **out)
+
+resnet_case("resnet18in_step", INBasicBlock, [2, 2, 2, 2], 2, 8, seed=54, make=lambda: ref_resnet18IN(2),
+            grad_probes=["conv1.weight", "bn1.weight", "bn1.bias", "class_classifier.weight", "class_classifier.bias", "layer1.0.conv1.weight",
+                         "layer2.0.downsample.0.weight", "layer4.%d.conv2.weight", "layer3.0.conv2.weight"],
+            state_probes=["bn1.weight", "bn1.bias"])
+
+if wanted("fed_loop_in"):
+    largs = types.SimpleNamespace(dg_method="no_DG", network="resnet18IN", n_classes=3, IN_test=False, jig_weight=0.0)
+    lmodel = ref_resnet.ResNetIN(INBasicBlock, [1, 1, 1, 1], classes=3)
+    lmodel.load_state_dict(R.seeded_state_dict(lmodel, 93))
+    logger = _StubLogger()
+    opt = torch.optim.SGD(params=lmodel.parameters(), lr=0.01)
+    loss_fun = nn.CrossEntropyLoss()
+    tr1 = nsl["train"](lmodel, train_loader, opt, loss_fun, 3, torch.device("cpu"), largs, 0, logger)
+    te1 = nsl["test"](lmodel, test_loader, loss_fun, torch.device("cpu"), largs)
+    tr2 = nsl["train"](lmodel, train_loader, opt, loss_fun, 3, torch.device("cpu"), largs, 1, logger)
+    te2 = nsl["test"](lmodel, train_loader, loss_fun, torch.device("cpu"), largs)
+    lsd = lmodel.state_dict()
+    keys, ksum, kabs = key_stats(lsd)
+    save("fed_loop_in", seed=93, train_seeds=[100, 101, 102], train_sizes=[4, 4, 3], test_seeds=[200, 201], test_sizes=[4, 2], lr=0.01,
+         train1=np.array(tr1, dtype=np.float64), test1=np.array(te1, dtype=np.float64),
+         train2=np.array(tr2, dtype=np.float64), test2=np.array(te2, dtype=np.float64),
+         log_loss=np.array([r[2] for r in logger.rows], dtype=np.float64), log_right=np.array([r[3] for r in logger.rows]),
+         conv1_head=lsd["conv1.weight"].flatten()[:64], fc_weight=lsd["class_classifier.weight"], fc_bias=lsd["class_classifier.bias"],
+         bn1_weight=lsd["bn1.weight"], bn1_bias=lsd["bn1.bias"], keys=keys, key_sum=ksum, key_abs=kabs)
+
+if wanted("in_test"):
+    iargs = types.SimpleNamespace(dg_method="no_DG", network="resnet18", n_classes=3, IN_test=True, jig_weight=0.0, mode="fedavg")
+    out = {}
+    for tag, block, layers, classes, seed in (("r18", R.BasicBlock, [1, 1, 1, 1], 3, 94), ("r50", R.Bottleneck, [3, 4, 6, 3], 7, 95)):
+        m = ref_resnet.ResNet(block, layers, classes=classes)
+        m.load_state_dict(R.seeded_state_dict(R.ResNet(block, layers, classes=classes), seed))
+        bn_copy = copy.deepcopy(m)
+        loader = [R.synth_batch(n, 222, classes, seed=300 + seed + i) for i, n in enumerate((4, 2))]
+        r1 = nsl["test"](m, loader, nn.CrossEntropyLoss(), torch.device("cpu"), iargs)
+        keys, ksum, kabs = key_stats(m.state_dict())
+        r2 = nsl["test"](m, loader, nn.CrossEntropyLoss(), torch.device("cpu"), iargs)
+        out.update({tag + "/seed": seed, tag + "/classes": classes, tag + "/test1": np.array(r1, dtype=np.float64),
+                    tag + "/test2": np.array(r2, dtype=np.float64), tag + "/keys": keys, tag + "/key_sum": ksum, tag + "/key_abs": kabs,
+                    tag + "/bn_keys": np.array(list(bn_copy.state_dict().keys()))})
+        if tag == "r18":
+            # the reference's communication() (fedavg) right after: the swapped server, three perturbed BatchNorm clients
+            clients = [copy.deepcopy(bn_copy) for _ in range(3)]
+            for ci, c in enumerate(clients):
+                rs = np.random.RandomState(400 + ci)
+                with torch.no_grad():
+                    for k, v in c.state_dict().items():
+                        if "num_batches_tracked" in k:
+                            v.fill_(5 + ci)
+                        else:
+                            v += torch.from_numpy(rs.normal(0, 0.02, tuple(v.shape)).astype(np.float32))
+            srv, clients = nsf["communication"](iargs, m, clients, [0.5, 0.3, 0.2])
+            keys, ksum, kabs = key_stats(srv.state_dict())
+            out.update({"comm/server_keys": keys, "comm/server_sum": ksum, "comm/server_abs": kabs})
+            for ci, c in enumerate(clients):
+                keys, ksum, kabs = key_stats(c.state_dict())
+                out.update({"comm/client_keys": keys, "comm/client%d_sum" % ci: ksum, "comm/client%d_abs" % ci: kabs})
+    save("in_test", weights=[0.5, 0.3, 0.2], **out)
 # --------------------------------------------------------------------------
 # Data plane lists (data/data_helper.py:46-159, data/ImageLoader.py:13-47): the reference's own get_train_dataloader /
 # get_test_dataloader / creat_train_loader_list / get_random_subset, AST-extracted, with the image datasets replaced by
